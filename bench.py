@@ -5,19 +5,32 @@ Workload (BASELINE.json configs[2]): the Book-1 final scene (reference CLI scene
 1200x675, 1000 samples per pixel, max depth 50 — exactly `./main 1 1200 1000 _` of the reference.
 A "step" is one full frame: every pixel's 1000-sample path loop over that GPU's rows -- the launch
 rt_render_rows_async makes (cost pre-pass, device-side plan, chain kernel, fold).  The scene arrays
-are resident in HBM before timing starts; the frame stays in HBM.  At N=1, after timing, rank 0 also
-times the drop-in boundary end to end (rt_render: flatten-free upload, launch, D2H into a host
-buffer, i.e. what Camera_render does after rt_flatten) and reports it as "end_to_end" -- never as
-"value".
+are resident in HBM before timing starts; the frame stays in HBM.
+
+A plain run (bench.py --gpus 1 --steps K --warmup W) does only what the headline figure needs: set up,
+warm up, time the K steps, write the outputs when --dump-outputs is given, print the result line.
+Everything else below runs only with --full, and fills "cpu_baseline", "vs_baseline", "parity" and
+"end_to_end" of the line (null in a plain run).
+
+--dump-outputs DIR: after the timed steps, the rows the last timed step left in this rank's frame buffer
+(what a caller of rt_render_rows_async receives) are written as DIR/frame.npy (N=1) or
+DIR/frame_rank<r>.npy, float32 holding the uint8 channel values, at most 64 MB over all ranks (a larger
+output is written as a fixed, seeded sample of its elements).  The scene and the per-pixel random streams
+are seeded constants, so the same arguments give the same inputs in every run and two builds can be
+compared file for file.
+
+--full: after timing, every rank also times the drop-in boundary end to end (rt_render_share: flatten-free
+upload, launch, D2H into a host buffer, i.e. what Camera_render does after rt_flatten) and reports it as
+"end_to_end" -- never as "value".
 
 Multi-GPU (python -m torch.distributed.run --nproc-per-node N bench.py --gpus N): one process per
 GPU, rows j % N == rank, no collective on the data path; the frame is fixed, so this
 is strong scaling.  Timing: barrier + synchronize on both sides of K steps, max over ranks.
 
-After timing (outside the timed region) the ranks' rows are gathered and the frame's sha256 is
+--full: after timing (outside the timed region) the ranks' rows are gathered and the frame's sha256 is
 compared with the reference render's (tests/golden/manifest.json) when that config has a golden.
 
-rank 0 at N=1 first times the reference's own CPU build (oracle/_ref/ref_render_fast: upstream
+--full: rank 0 at N=1 first times the reference's own CPU build (oracle/_ref/ref_render_fast: upstream
 `-std=c11 -Ofast -fopenmp`) on a bounded sample of the same workload, before the GPU is touched.
 """
 import argparse
@@ -56,7 +69,17 @@ def parse():
     ap.add_argument("--cpu-spp", type=int, default=100, help="spp of the bounded CPU-baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline, the parity check against the reference render and the "
+                         "end-to-end leg (each can still be switched off by its --no-... option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the rows of the last timed step as DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def cpu_baseline(args):
@@ -153,8 +176,27 @@ def pmc_for(config_key, kernel_name, build_id):
     return rel, None, "none"
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # of --dump-outputs, over all ranks
+
+
+def dump_outputs(path, rows, world):
+    """This rank's rows of the last timed step (uint8, (n_rows, W, 3)) as float32: whole when the ranks' files
+    together stay under DUMP_LIMIT_BYTES, else a fixed, seeded sample of its elements (flat order)."""
+    import numpy as np
+
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    out = rows.astype(np.float32)
+    limit = DUMP_LIMIT_BYTES // 4 // world - 64  # elements per rank (64: room for the .npy header)
+    if out.size > limit:
+        idx = np.sort(np.random.default_rng(19).choice(out.size, size=limit, replace=False))
+        out = out.reshape(-1)[idx]
+    np.save(path, out)
+
+
 def main():
     args = parse()
+    do_cpu = args.full and not args.no_cpu_baseline
+    do_parity = args.full and not args.no_parity
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -162,7 +204,7 @@ def main():
         print(f"warning: WORLD_SIZE={world} but --gpus {args.gpus}", file=sys.stderr)
 
     base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and do_cpu:
         base = cpu_baseline(args)  # before anything initialises the GPU
 
     import torch
@@ -238,9 +280,14 @@ def main():
     else:
         kernel_ms_max = kernel_ms
 
-    # ---- parity (outside the timed region): gather rows, compare the frame with the reference
+    # ---- the outputs of the last timed step (outside the timed region)
+    if args.dump_outputs:
+        name = "frame.npy" if world == 1 else f"frame_rank{rank}.npy"
+        dump_outputs(os.path.join(os.path.abspath(args.dump_outputs), name), buf[:n_rows].cpu().numpy(), world)
+
+    # ---- parity (--full, outside the timed region): gather rows, compare the frame with the reference
     parity = None
-    if not args.no_parity:
+    if do_parity:
         rows = buf[:n_rows]
         if world > 1:
             m = (H + world - 1) // world
@@ -278,7 +325,7 @@ def main():
     # main.c:334-338) for this rank's share.  "first": from an empty device-scene cache (a process's first
     # call); "warm": the same call again, the cached scene reused.  Max over ranks.
     e2e = None
-    if not args.no_parity:
+    if do_parity:
         import numpy as np
 
         host = np.zeros((H, W, 3), np.uint8)
@@ -331,12 +378,14 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": round(value / base["value"], 2) if base else None,
             "vs_baseline_source": ("cpu_baseline below: the reference's own -Ofast OpenMP build on this box's host "
-                                   "cores, same scene and size" if base else "no same-box CPU baseline in this run"),
+                                   "cores, same scene and size" if base else
+                                   "no same-box CPU baseline in this run (--full at N=1 measures one)"),
             "dtype": "f32",
             "data": "synthetic: the reference's procedural scene (pcg32 seed 19,29) and per-pixel pcg32 streams",
             "config": {"workload": workload, "scene": args.scene, "width": W, "height": H, "spp": spp,

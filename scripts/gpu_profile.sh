@@ -32,7 +32,7 @@ PY
 )
 BOX=$(python3 -c "import sys, json; sys.path.insert(0, 'ray-tracing-c_amd'); import rtc; print(json.dumps(rtc.box_identity()))")
 echo "config $KEY samples/frame $SAMPLES build $BID box $BOX"
-[ "${SKIP_BENCH:-0}" = 1 ] || step bench 900 python3 bench.py $CFG
+[ "${SKIP_BENCH:-0}" = 1 ] || step bench 900 python3 bench.py --full $CFG
 step stats 900 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${TAG}_stats -o run -- \
     python3 bench.py $CFG --steps 2 --warmup 1 --no-cpu-baseline --no-parity
 A="$CFG --steps 1 --warmup 1 --no-cpu-baseline --no-parity"  # (2 frames: the first pays one-time costs)

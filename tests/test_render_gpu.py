@@ -355,7 +355,7 @@ def test_bench_two_rank_launch_reassembles_reference_frame():
     env = dict(os.environ, RT_BENCH_SHARE_DEVICE="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "1", "--warmup", "0", "--spp", "10", "--no-cpu-baseline"]
+           "--gpus", "2", "--steps", "1", "--warmup", "0", "--spp", "10", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
