@@ -64,6 +64,50 @@ int rt_render_rows_async(rt_device_scene *dscene, int row0, int row_stride, int 
  * rt_render_rows_async cannot report this itself (it returns before the work runs). */
 int rt_scene_check(rt_device_scene *dscene);
 
+/* ---- ray queries: the batched form of the reference's per-object `hit` method
+ * (`world->objects.hittable.vtable->hit(objects, ray, tmin, tmax, &rec, rng)`, src/hittable.c:38-423).
+ * rt_trace_rays_async traces n caller-supplied rays against the resident scene and writes one rt_hit per
+ * ray: exactly the record the reference's call returns for that ray -- its visit order, shrinking t_max,
+ * the sphere's exclusive (tmin < t < tmax) and the quad's inclusive (tmin <= t <= tmax) bounds, and the
+ * fix-ups of enclosing Translate / RotateY objects.  u, v are always filled for spheres and quads.  The
+ * scene's camera, spp and max_depth play no part; every scene kind can be queried. */
+typedef struct rt_ray { /* 24 B, world space; d need not be unit length.  A direction of all zeros is the
+                         * caller's error, as in the reference: the result is then unspecified (no fault). */
+  float o[3], d[3];
+} rt_ray;
+typedef struct rt_hit { /* 48 B */
+  float t, p[3], normal[3], u, v;
+  int32_t material; /* index into the flat scene's materials; -1 on a miss */
+  int32_t prim;     /* winning SPHERE / QUAD / MEDIUM ref (rt_flat.h encoding); RT_REF_NONE on a miss */
+  uint32_t flags;   /* RT_HIT_FRONT_FACE, RT_HIT_IN_MEDIUM */
+} rt_hit;
+#define RT_HIT_FRONT_FACE 1u /* bit 0: the ray met the surface from outside (HitRecord.front_face) */
+#define RT_HIT_IN_MEDIUM 2u  /* bit 1: the hit is a scattering point inside a ConstantMedium */
+/* A miss writes t = +inf, prim = RT_REF_NONE, material = -1 and zeros elsewhere.  For a hit inside a
+ * ConstantMedium the reference leaves normal / front_face / u / v stale (src/hittable.c:392-423); here they
+ * are defined: normal = u = v = 0, RT_HIT_FRONT_FACE and RT_HIT_IN_MEDIUM set, material = the medium's
+ * phase function, prim = the MEDIUM ref. */
+typedef struct rt_query_params {
+  float tmin, tmax;            /* tmax may be +inf; NaN or tmin > tmax is an error */
+  uint64_t rng_state, rng_seq; /* ray k draws from pcg32_seed(rng_state, rng_seq + k); only a ConstantMedium
+                                * consumes it, so a query is reproducible and independent of batch order.
+                                * rng_seq + n must not exceed 2^31 (the device keeps the stream selector
+                                * in 32 bits). */
+} rt_query_params;
+
+/* d_rays (8-byte aligned) and d_hits (16-byte aligned) are device pointers on the scene's device.
+ * Asynchronous on `stream` (NULL = the device's default stream), no host synchronisation; like
+ * rt_render_rows_async it first waits, on the device, for the scene's previous launch and is waited for
+ * by the next, but it shares no scratch with the renders.  For a scene whose render path keeps no
+ * traversal preorder on the device (Book-1 scenes), the first query allocates one and queues the copy of
+ * what rt_scene_upload kept on the host; a scene that is never queried costs nothing on the device.
+ * n == 0 returns 0 without a launch; a NULL pointer, n < 0 or a bad t range return -1. */
+int rt_trace_rays_async(rt_device_scene *dscene, const rt_ray *d_rays, int64_t n, const rt_query_params *params,
+                        rt_hit *d_hits, void *stream);
+/* Synchronous convenience over host buffers (copy in, trace, copy back). */
+int rt_trace_rays(rt_device_scene *dscene, const rt_ray *rays_host, int64_t n, const rt_query_params *params,
+                  rt_hit *hits_host);
+
 /* Whole frame into a host buffer (width*height*3), rows interleaved j mod n_gpus over GPUs
  * 0..n_gpus-1 (n_gpus <= 0: all visible), no collectives.  The host-side preprocessing of the scene
  * runs once; then one host thread per GPU uploads, launches on its own stream, copies its rows back

@@ -442,13 +442,14 @@ struct PreTrace {
   bool found;
   Hit h;
 };
-RT_D void pre_begin(PreTrace &T, f3 wo, f3 wd) {
+// tmax: the caller's upper bound of t (a ray query's, rt_query.h; the render's rays have none)
+RT_D void pre_begin(PreTrace &T, f3 wo, f3 wd, float tmax = __builtin_inff()) {
   T.o = wo, T.d = wd;
   T.inv = mk(1.0f / wd.x, 1.0f / wd.y, 1.0f / wd.z);
   T.dd = dot(wd, wd);
   T.ra = recip_core(T.dd);
   T.fast = T.dd >= kDivLo && T.dd <= kDivHi;
-  T.tmax = __builtin_inff();
+  T.tmax = tmax;
   T.frame = RT_REF_NONE;
   T.p = 0u, T.fend = 0xffffffffu, T.fpos = 0u;
   T.found = false;
@@ -654,7 +655,8 @@ RT_D bool mat_uses_uv(const DScene &S, int32_t mat) {
 
 // Rebuild the winner's HitRecord exactly as its hit() wrote it, then apply the enclosing
 // transforms' fix-ups innermost-first (RotateY_hit / Translate_hit post-processing).
-template <int F>
+// kForceUV: a sphere's u, v whatever its material reads (a ray query returns them: rt_query.h).
+template <int F, bool kForceUV = false>
 RT_D void make_record(const DScene &S, f3 wo, f3 wd, const Hit &h, Rec &r) {
   f3 o = wo, d = wd;
   if ((F & RT_FEAT_XFORM) && h.xform != RT_REF_NONE) local_ray(S, h.xform, wo, wd, o, d);
@@ -671,7 +673,7 @@ RT_D void make_record(const DScene &S, f3 wo, f3 wd, const Hit &h, Rec &r) {
     r.normal = r.front ? outward : neg(outward);
     // u, v (glibc-exact atan2f / acosf ports) only where the material's texture reads them (image,
     // checker): every other texture ignores u, v, so skipping them changes no output
-    if ((F & RT_FEAT_TEX_UV) && mat_uses_uv(S, s.material)) {
+    if (kForceUV || ((F & RT_FEAT_TEX_UV) && mat_uses_uv(S, s.material))) {
       r.u = (rtm::atan2f(-outward.z, outward.x) + kPi) * kInvPi * 0.5f;
       r.v = rtm::acosf(-outward.y) * kInvPi;
     }

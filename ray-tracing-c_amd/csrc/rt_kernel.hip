@@ -11,6 +11,9 @@
 //   rt_book1_kernel        Book-1 scenes at low spp / small images, lane = pixel (or RT_MODE=lane)
 //   rt_book1_cost_kernel   the low-spp pre-pass that measures every pixel's cost
 //   rt_general_kernel      every other scene (Book-2 features)
+//   rt_query_naive_kernel  closest-hit queries of caller-supplied rays on any scene (rt_trace_rays_async;
+//                          compiled in rt_query.hip, a translation unit of its own, so that the kernels
+//                          above compile to what they compile to without it)
 // Every tuning knob (RT_* environment variables) is read once, at scene upload.
 #include <hip/hip_runtime.h>
 
@@ -33,6 +36,7 @@
 #include "../../include/rt_hip.h"
 #include "rt_book1.h"
 #include "rt_general.h"
+#include "rt_query.h"
 #include "rt_device.h"
 
 using namespace rt;
@@ -682,6 +686,11 @@ enum : int { kModeLane = 0, kModeChain = 2, kModeAuto = 3 };
 struct Config {
   bool book1 = true, book1_lds = true, general = true, gen_pre = true;
   bool lpt = true, bf = true, bf_cuts = true, px_time = false, debug = false;
+  // ray queries: the one-ray-per-thread launch, or (RT_QUERY_NAIVE=0) the persistent kernel, its entries
+  // per refill round (RT_QUERY_STEPS) and the most preorder entries it stages in LDS (RT_QUERY_LDS; < 0: all
+  // that fit) -- measured slower on every batch of scripts/query_probe.py
+  bool query_naive = true;
+  int query_steps = qry::kSteps, query_lds = -1;
   bool pre_resume = true;     // chain items go on from the cost pre-pass's samples (RT_PRE_RESUME=0: off)
   int lpt_spp = 16, shade_batch = 48;
   // the chain launch's cost pre-pass spp (capped at a quarter of the frame's; lpt_spp is the least a chain
@@ -788,6 +797,10 @@ struct Config {
     c.book1_lds = env_flag("RT_BOOK1_LDS", true);
     c.general = env_flag("RT_GENERAL", true);
     c.gen_pre = env_flag("RT_GEN_PRE", true);
+    c.query_naive = env_flag("RT_QUERY_NAIVE", true);
+    c.query_steps = env_int("RT_QUERY_STEPS", c.query_steps);
+    if (c.query_steps < 1) c.query_steps = 1;
+    c.query_lds = env_int("RT_QUERY_LDS", c.query_lds);
     c.lpt = env_flag("RT_LPT", true);
     c.pre_resume = env_flag("RT_PRE_RESUME", true);
     c.bf = env_flag("RT_BF", true);
@@ -903,6 +916,15 @@ struct rt_device_scene {
   int gen_lds = 0;
   size_t gen_lds_bytes = 0;   // dynamic LDS of the general kernel
   int32_t gen_perlin_lds = -1;  // byte offset of the Perlin tables in it, or -1
+  // ray queries (rt_query.h).  The preorder is kept on the host at upload when the render path put none
+  // on the device (Book-1 scenes, deep paths, RT_GEN_PRE=0); the first query makes the device copy and
+  // the work counter, so a scene that is never queried allocates and copies nothing for them.
+  std::vector<float4> q_pre_host;
+  bool q_ready = false;
+  void *q_arena = nullptr;  // the persistent kernel's work counter (256 B), then the query's preorder copy if it needs one
+  qry::QueryView qview;
+  int q_grid = 0, q_block = 0;  // the persistent kernel's launch shape (diagnostic build)
+  size_t q_lds_bytes = 0;
 };
 
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -1415,6 +1437,8 @@ static rt_device_scene *upload_packed(const rt_flat_scene *s, const HostPack &H,
     }
     d->view.pre = (const float4 *)d->pre_arena;
     d->view.n_pre = (int32_t)(H.pre.size() / 2);
+  } else {
+    build_preorder(*s, d->q_pre_host);  // for ray queries (host only until the first one)
   }
   // status words (256 B), then the launch timestamp ring
   const size_t status_bytes = 256 + rt_device_scene::kLaunchRing * 2 * sizeof(uint64_t);
@@ -1473,6 +1497,7 @@ extern "C" void rt_scene_release(rt_device_scene *d) {
   if (d->mig_q) (void)hipFree(d->mig_q);
   if (d->deep_rec) (void)hipFree(d->deep_rec);
   if (d->pre_arena) (void)hipFree(d->pre_arena);
+  if (d->q_arena) (void)hipFree(d->q_arena);
   if (d->ch_arena) (void)hipFree(d->ch_arena);
   if (d->ch_rec_arena) (void)hipFree(d->ch_rec_arena);
   if (d->rec_demand_host) (void)hipHostFree(d->rec_demand_host);
@@ -2009,6 +2034,117 @@ extern "C" int rt_scene_check(rt_device_scene *d) {
   HIP_OK(hipMemset(d->status, 0, sizeof st));
   return rt_set_error("render incomplete on device %d: %u work item(s) of a chain launch never finished "
                       "(status 0x%x); the frame is not valid", d->device, st[1], st[0]), -1;
+}
+
+// ------------------------------------------------------------------------------ ray queries
+// Queries need only the traversal features: a scene of spheres under BVHs and lists runs the Book-1
+// instantiation whatever its materials and textures are.
+static bool query_book1(const rt_device_scene *d) {
+  return (d->features & (RT_FEAT_QUAD | RT_FEAT_XFORM | RT_FEAT_MEDIUM)) == 0;
+}
+// The first query of a scene: the device copy of the preorder where the render path has none (queued on
+// `st`, from the host copy kept at upload); for the persistent kernel its work counter and launch shape.
+static int query_prepare(rt_device_scene *d, hipStream_t st) {
+  const bool own_pre = d->view.pre == nullptr;
+  const size_t pre_bytes = own_pre ? d->q_pre_host.size() * sizeof(float4) : 0;
+  qry::QueryView &V = d->qview;
+  memset(&V, 0, sizeof V);
+  V.S = d->view;
+  if (pre_bytes || !d->cfg.query_naive) {
+    HIP_OK(hipMalloc(&d->q_arena, 256 + pre_bytes));
+    V.counter = (unsigned long long *)d->q_arena;
+  }
+  if (own_pre) {
+    if (pre_bytes)
+      HIP_OK(hipMemcpyAsync((char *)d->q_arena + 256, d->q_pre_host.data(), pre_bytes, hipMemcpyHostToDevice, st));
+    V.S.pre = pre_bytes ? (const float4 *)((char *)d->q_arena + 256) : nullptr;
+    V.S.n_pre = (int32_t)(d->q_pre_host.size() / 2);
+  }
+#ifdef RT_DIAG
+  if (!d->cfg.query_naive) {  // the persistent kernel's launch shape
+    hipDeviceProp_t prop;
+    HIP_OK(hipGetDeviceProperties(&prop, d->device));
+    const size_t all_bytes = (size_t)V.S.n_pre * 2 * sizeof(float4);
+    const bool big = all_bytes > qry::kLdsSmall && (size_t)prop.sharedMemPerBlock > qry::kLdsSmall;
+    const size_t cap = big ? (size_t)prop.sharedMemPerBlock : qry::kLdsSmall;
+    V.n_lds = (uint32_t)((all_bytes < cap ? all_bytes : cap) / (2 * sizeof(float4)));
+    if (d->cfg.query_lds >= 0 && (uint32_t)d->cfg.query_lds < V.n_lds) V.n_lds = (uint32_t)d->cfg.query_lds;
+    V.steps = d->cfg.query_steps;
+    d->q_lds_bytes = (size_t)V.n_lds * 2 * sizeof(float4);
+    d->q_block = big ? qry::kBigBlock : qry::kBlock;
+    const void *fn = qry::kernel_fn(query_book1(d), big);
+    if (d->q_lds_bytes > 65536)
+      HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->q_lds_bytes));
+    int per_cu = 0;
+    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, d->q_block, d->q_lds_bytes));
+    if (per_cu < 1) per_cu = 1;
+    d->q_grid = prop.multiProcessorCount * per_cu;
+  }
+#endif
+  d->q_ready = true;
+  return 0;
+}
+
+extern "C" int rt_trace_rays_async(rt_device_scene *d, const rt_ray *d_rays, int64_t n, const rt_query_params *prm,
+                                   rt_hit *d_hits, void *stream) {
+  static_assert(sizeof(rt_ray) == 24 && sizeof(rt_hit) == 48, "rt_ray / rt_hit layout");
+  if (!d || !prm) return rt_set_error("rt_trace_rays_async: NULL argument"), -1;
+  if (n < 0) return rt_set_error("rt_trace_rays_async: n = %lld < 0", (long long)n), -1;
+  if (prm->tmin != prm->tmin || prm->tmax != prm->tmax || prm->tmin > prm->tmax)
+    return rt_set_error("rt_trace_rays_async: bad t range [%g, %g]", (double)prm->tmin, (double)prm->tmax), -1;
+  if (prm->rng_seq >= (1ull << 31) || (uint64_t)n > (1ull << 31) - prm->rng_seq)
+    return rt_set_error("rt_trace_rays_async: rng_seq + n exceeds 2^31"), -1;
+  if (n == 0) return 0;
+  if (!d_rays || !d_hits) return rt_set_error("rt_trace_rays_async: NULL argument"), -1;
+  if (((uintptr_t)d_rays & 7u) || ((uintptr_t)d_hits & 15u))
+    return rt_set_error("rt_trace_rays_async: rays must be 8-byte and hits 16-byte aligned"), -1;
+  HIP_OK(hipSetDevice(d->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (d->launched) HIP_OK(hipStreamWaitEvent(st, d->ev_done, 0));
+  if (!d->q_ready && query_prepare(d, st) != 0) return -1;
+  qry::QueryView V = d->qview;
+  V.rays = (const float2 *)d_rays;
+  V.hits = (float4 *)d_hits;
+  V.n = n;
+  V.tmin = prm->tmin;
+  V.tmax = prm->tmax;
+  V.rng_state = prm->rng_state;
+  V.rng_seq = prm->rng_seq;
+  const bool fb = query_book1(d);
+#ifdef RT_DIAG
+  if (!d->cfg.query_naive) {
+    HIP_OK(hipMemsetAsync(V.counter, 0, sizeof(unsigned long long), st));
+    // no more workgroups than the rays can occupy
+    const int64_t need = (n + d->q_block - 1) / d->q_block;
+    qry::launch(fb, d->q_block == qry::kBigBlock, (unsigned)(need < d->q_grid ? need : d->q_grid), d->q_lds_bytes, st, V);
+  } else
+#endif
+    qry::launch_naive(fb, st, V);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipEventRecord(d->ev_done, st));
+  d->launched = true;
+  return 0;
+}
+
+// Synchronous convenience over host buffers: copies the rays in, traces, copies the hits back.
+extern "C" int rt_trace_rays(rt_device_scene *d, const rt_ray *rays_host, int64_t n, const rt_query_params *prm,
+                             rt_hit *hits_host) {
+  if (!d || !prm) return rt_set_error("rt_trace_rays: NULL argument"), -1;
+  if (n > 0 && (!rays_host || !hits_host)) return rt_set_error("rt_trace_rays: NULL argument"), -1;
+  if (n <= 0) return rt_trace_rays_async(d, nullptr, n, prm, nullptr, nullptr);  // (0, or the error for n < 0)
+  HIP_OK(hipSetDevice(d->device));
+  char *buf = nullptr;
+  const size_t rb = align_up((size_t)n * sizeof(rt_ray), 256), hb = (size_t)n * sizeof(rt_hit);
+  HIP_OK(hipMalloc((void **)&buf, rb + hb));
+  int rc = -1;
+  if (hipMemcpy(buf, rays_host, (size_t)n * sizeof(rt_ray), hipMemcpyHostToDevice) != hipSuccess) {
+    rt_set_error("rt_trace_rays: copying the rays to device %d failed", d->device);
+  } else if (rt_trace_rays_async(d, (const rt_ray *)buf, n, prm, (rt_hit *)(buf + rb), nullptr) == 0) {
+    if (hipMemcpy(hits_host, buf + rb, hb, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;  // (waits for the launch)
+    else rt_set_error("rt_trace_rays: copying the hits back from device %d failed", d->device);
+  }
+  (void)hipFree(buf);
+  return rc;
 }
 
 // ------------------------------------------------------------------------------ device-scene cache

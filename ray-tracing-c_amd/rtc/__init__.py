@@ -74,7 +74,16 @@ class RtFlatScene(ctypes.Structure):
                 + [(n, c_void_p) for n in _ARRAYS])
 
 
+class RtQueryParams(ctypes.Structure):
+    """rt_query_params (include/rt_hip.h)."""
+    _fields_ = [("tmin", c_float), ("tmax", c_float), ("rng_state", ctypes.c_uint64), ("rng_seq", ctypes.c_uint64)]
+
+
+REF_NONE = -1                      # RT_REF_NONE: Hits.prim of a miss
+HIT_FRONT_FACE, HIT_IN_MEDIUM = 1, 2  # rt_hit.flags
+
 assert ctypes.sizeof(RtCamera) == 128
+assert ctypes.sizeof(RtQueryParams) == 24
 assert RtFlatScene.n_image_bytes.offset == 192
 
 
@@ -182,6 +191,12 @@ def lib() -> ctypes.CDLL:
         L.rt_build_id.restype = c_char_p
         L.rt_scene_chain_diag.argtypes = [c_void_p, c_void_p, c_int64]
         L.rt_scene_chain_diag.restype = c_int64
+        if hasattr(L, "rt_trace_rays_async"):  # (older builds loaded through RTC_LIB for an A/B lack these)
+            QP = POINTER(RtQueryParams)
+            L.rt_trace_rays_async.argtypes = [c_void_p, c_void_p, c_int64, QP, c_void_p, c_void_p]
+            L.rt_trace_rays_async.restype = c_int
+            L.rt_trace_rays.argtypes = [c_void_p, c_void_p, c_int64, QP, c_void_p]
+            L.rt_trace_rays.restype = c_int
         _libs[path] = L
     return _libs[path]
 
@@ -312,6 +327,61 @@ def last_kernel_ms(device: int = 0) -> float:
     return lib().rt_last_kernel_ms(device)
 
 
+class Hits:
+    """The rt_hit records of a ray query (include/rt_hip.h): ``raw`` is the (n, 12) int32 array -- a torch
+    tensor on the scene's device (DeviceScene.trace_rays) or a numpy array (trace_rays_host) -- and the
+    properties are typed views of its columns (no copies): t, p (n, 3), normal (n, 3), uv (n, 2), material,
+    prim (rt_flat.h ref encoding, REF_NONE on a miss), front and in_medium (bool)."""
+
+    def __init__(self, raw):
+        self.raw = raw
+        if isinstance(raw, np.ndarray):
+            self._f = raw.view(np.float32)
+        else:
+            import torch
+
+            self._f = raw.view(torch.float32)
+
+    def __len__(self):
+        return int(self.raw.shape[0])
+
+    @property
+    def t(self):
+        return self._f[:, 0]
+
+    @property
+    def p(self):
+        return self._f[:, 1:4]
+
+    @property
+    def normal(self):
+        return self._f[:, 4:7]
+
+    @property
+    def uv(self):
+        return self._f[:, 7:9]
+
+    @property
+    def material(self):
+        return self.raw[:, 9]
+
+    @property
+    def prim(self):
+        return self.raw[:, 10]
+
+    @property
+    def front(self):
+        return (self.raw[:, 11] & HIT_FRONT_FACE) != 0
+
+    @property
+    def in_medium(self):
+        return (self.raw[:, 11] & HIT_IN_MEDIUM) != 0
+
+
+def _query_params(tmin, tmax, rng) -> RtQueryParams:
+    return RtQueryParams(float(tmin), float(tmax), int(rng[0]), int(rng[1]))
+
+
 class DeviceScene:
     """Scene arrays resident in one GPU's HBM (rt_scene_upload)."""
 
@@ -328,6 +398,27 @@ class DeviceScene:
                                           c_void_p(int(d_out_ptr)), c_void_p(int(stream_ptr)))
         if rc != 0:
             raise RtcError(f"rt_render_rows_async failed: {last_error(self._L)}")
+
+    def trace_rays(self, rays, tmin: float = 1e-3, tmax: float = float("inf"), rng=(0, 0), stream_ptr: int = 0) -> Hits:
+        """Closest hits of `rays` -- a contiguous float32 (n, 6) torch tensor of (origin, direction) rows on
+        this scene's device -- as the reference's ``hit(ray, tmin, tmax, &rec, rng)`` on the world's objects
+        returns them (rt_trace_rays_async).  Asynchronous on `stream_ptr` (0: the device's default stream);
+        ray k's rng is pcg32 seeded (rng[0], rng[1] + k)."""
+        import torch
+
+        if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2
+                and rays.shape[1] == 6 and rays.is_contiguous()):
+            raise ValueError("rays must be a contiguous float32 (n, 6) tensor on the scene's device")
+        if rays.device.index != self.device:
+            raise ValueError(f"rays are on {rays.device}, the scene on device {self.device}")
+        n = int(rays.shape[0])
+        hits = torch.empty((n, 12), dtype=torch.int32, device=rays.device)
+        prm = _query_params(tmin, tmax, rng)
+        rc = self._L.rt_trace_rays_async(self._h, c_void_p(rays.data_ptr()), n, ctypes.byref(prm),
+                                         c_void_p(hits.data_ptr()), c_void_p(int(stream_ptr)))
+        if rc != 0:
+            raise RtcError(f"rt_trace_rays_async failed: {last_error(self._L)}")
+        return Hits(hits)
 
     def check(self):
         """Wait for this scene's launches and raise RtcError if any work item never finished
@@ -374,6 +465,20 @@ class DeviceScene:
             self.close()
         except Exception:
             pass
+
+
+def trace_rays_host(dscene: DeviceScene, rays: np.ndarray, tmin: float = 1e-3, tmax: float = float("inf"),
+                    rng=(0, 0)) -> Hits:
+    """The synchronous query over host buffers (rt_trace_rays): `rays` is a float32 (n, 6) numpy array."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32)
+    if rays.ndim != 2 or rays.shape[1] != 6:
+        raise ValueError("rays must be a float32 (n, 6) array")
+    hits = np.empty((rays.shape[0], 12), dtype=np.int32)
+    prm = _query_params(tmin, tmax, rng)
+    rc = dscene._L.rt_trace_rays(dscene._h, rays.ctypes.data, rays.shape[0], ctypes.byref(prm), hits.ctypes.data)
+    if rc != 0:
+        raise RtcError(f"rt_trace_rays failed: {last_error(dscene._L)}")
+    return Hits(hits)
 
 
 def box_identity(device: int = 0) -> dict:
